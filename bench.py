@@ -15,11 +15,23 @@ data.rs:161-206) over one batch of data files already resident in HBM.
           through the library's C ABI (cask_keydir_gather_rccl), timed separately.
 
 Rank 0 prints one JSON line with the roofline of the dominant kernel (k_run_hash on these shapes,
-HIP events inside the library on the stream it launches on) and, at N = 1, the CPU baseline (the
-oracle's reference-faithful replay of a bounded sample of the same files, timed on this host).
-Secondary numbers (configs[1], host-resident end to end) go in extra keys, never in `value`.
+HIP events inside the library on the stream it launches on, read in the timed steps themselves).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does only what the headline needs: it generates the files, makes one call (the row
+count must be the generator's), warms up, times the K steps, writes the outputs if asked, prints
+the line. Everything else is behind --full: the row-for-row check against the generator before
+timing, cold_call_ms, the read-only stream ceiling, at N = 1 the CPU baseline (the oracle's
+reference-faithful replay of a bounded sample of the same files, timed on this host), the
+host-resident end-to-end rate, configs[1] and the configs[4] shard on one GPU, at N > 1 the keydir
+gather and the cfg5 shard. Secondary numbers go in extra keys, never in `value`; the --no-* options
+drop single ones from a --full run.
+
+--dump-outputs DIR writes what the last timed step left in the caller's row arrays (DIR/<name>.npy,
+float64): `count`, a fixed seeded sample of the rows (`sample_index` and the five columns at those
+rows) and `column_sums` over all of them. The files are generated from fixed seeds, so two builds
+run with the same arguments can be compared array for array.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...      (driver, N>1)
 
 Every CASK_* variable in the environment is printed in the line; the library's tuning knobs are
@@ -52,6 +64,12 @@ def parse():
     # (a step is ~8 ms: 50 steps keep host hiccups out of the number and still take 0.4 s)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (see the module docstring); "
+                         "off by default: a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows the last timed step produced (count, a seeded sample, column sums) "
+                         "as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-files", type=int, default=2, help="configs[2] files timed by the CPU baseline")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-resident (H2D+D2H) measurement")
@@ -225,12 +243,55 @@ def check_rows(torch, rows, res, files, vsz, rl, first_seq):
         assert bool((rows["pos"][res.file_row_offset[i]:res.file_row_offset[i + 1]].to(torch.int64) == want).all()), i
 
 
+DUMP_SAMPLE_ROWS = 1_000_000  # 6 float64 arrays of this length: 48 MB, under the 64 MB a dump may take
+DUMP_SEED = 0xD0E5
+ROW_COLUMNS = ("pos", "seq", "ksz", "vsz", "status")
+
+
+def dump_outputs(torch, outdir, rows, count, prefix="", sample_rows=DUMP_SAMPLE_ROWS):
+    """Write the first `count` rows of the caller's row arrays (what a cask_scan_device caller
+    receives) under `outdir` as float64 .npy files: `count`, `sample_index` (min(count, sample_rows)
+    distinct row numbers drawn from a fixed seed, ascending; every row when count is not larger),
+    one array per column holding that column at those rows, and `column_sums` — per column, in
+    ROW_COLUMNS' order, the wrapping 64-bit sum of the column and of column[i] * (i + 1) over all
+    count rows, each as its low and high 32 bits (exact in float64), so that a difference outside
+    the sample, or rows in another order, still shows. Every value written is an integer below
+    2^53. Returns the bytes written."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    count = int(count)
+    if count > sample_rows:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(count, size=sample_rows, replace=False))
+    else:
+        idx = np.arange(count, dtype=np.int64)
+    out = {"count": np.array([count], dtype=np.float64), "sample_index": idx.astype(np.float64)}
+    dev = rows["pos"].device
+    didx = torch.from_numpy(idx.astype(np.int64)).to(dev)
+    weight = torch.arange(1, count + 1, dtype=torch.int64, device=dev)
+    sums = np.zeros((len(ROW_COLUMNS), 4), dtype=np.float64)
+    for c, name in enumerate(ROW_COLUMNS):
+        col = rows[name][:count].to(torch.int64)
+        out[name] = col[didx].cpu().numpy().astype(np.float64)
+        for k, v in enumerate((int(col.sum().item()), int((col * weight).sum().item()))):
+            v &= 0xFFFFFFFFFFFFFFFF
+            sums[c, 2 * k], sums[c, 2 * k + 1] = v & 0xFFFFFFFF, v >> 32
+        del col
+    out["column_sums"] = sums
+    written = 0
+    for name, a in out.items():
+        np.save(os.path.join(outdir, f"{prefix}{name}.npy"), a)
+        written += a.nbytes
+    return written
+
+
 def time_loop(torch, dev, run, timings, steps, barrier, dist, backend):
+    """(wall seconds of the steps, each step's phase times, the last step's row count)"""
     tbuf = [(C.c_float * 8)() for _ in range(steps)]
+    count = None
     barrier()
     t0 = time.perf_counter()
     for i in range(steps):
-        run()
+        count = run()
         timings(tbuf[i])
     barrier()
     elapsed = time.perf_counter() - t0
@@ -238,7 +299,7 @@ def time_loop(torch, dev, run, timings, steps, barrier, dist, backend):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    return elapsed, [[float(x) for x in t] for t in tbuf]
+    return elapsed, [[float(x) for x in t] for t in tbuf], count
 
 
 def secondary(extra: dict, key: str, fn):
@@ -267,7 +328,7 @@ def cfg1_secondary(ctx, torch, dev, steps):
     run, timings = ctx.prepare_scan(views, rows)
     for _ in range(3):
         run()
-    el, tt = time_loop(torch, dev, run, timings, steps, lambda: torch.cuda.synchronize(dev), None, "nccl")
+    el, tt, _ = time_loop(torch, dev, run, timings, steps, lambda: torch.cuda.synchronize(dev), None, "nccl")
     nb = sum(f.data.numel() for f in fs)
     k = sum(t[1] for t in tt) / len(tt)
     out = {"gibps": nb * steps / el / 2 ** 30, "ms_per_step": el * 1e3 / steps, "kernel": "k_scan_chunks",
@@ -296,7 +357,7 @@ def cfg4_shard_n1_secondary(ctx, torch, dev, steps):
     run, timings = ctx.prepare_scan(views, rows)
     for _ in range(3):
         run()
-    el, tt = time_loop(torch, dev, run, timings, steps, lambda: torch.cuda.synchronize(dev), None, "nccl")
+    el, tt, _ = time_loop(torch, dev, run, timings, steps, lambda: torch.cuda.synchronize(dev), None, "nccl")
     nb = sum(f.data.numel() for f, _ in files)
     k = sum(t[1] for t in tt) / len(tt)
     out = {"workload": "configs[4] shard of rank 0: 32 x 1 GiB data files, configs[2]'s record distribution "
@@ -339,7 +400,7 @@ def cfg5_shard_secondary(ctx, torch, dev, rank, world, dist, backend, same_devic
     assert int((rows["status"][:n] != 0).sum().item()) == 0
     run, timings = ctx.prepare_scan(views, rows)
     run()
-    el, _ = time_loop(torch, dev, run, timings, steps, barrier, dist, backend)
+    el, _, _ = time_loop(torch, dev, run, timings, steps, barrier, dist, backend)
     out["scan_gibps_all_ranks"] = nbytes * world * steps / el / 2 ** 30
     out["scan_ms_per_step"] = el * 1e3 / steps
     res = ctx.scan_device(views, rows)
@@ -458,10 +519,12 @@ def main():
     nfiles = len(views)
     rows = ctx.alloc_rows(n + 16)
 
-    # correctness gate before timing (every rank): rows equal the generator's records
+    # the first call (every rank): as many rows as the generator made records, none failing; under
+    # --full the correctness gate before timing too: rows equal the generator's records
     res = ctx.scan_device(views, rows)
-    assert res.count == n, (res.count, n)
-    check_rows(torch, rows, res, files, vsz, rl, first_seq)
+    assert res.count == n and res.error is None, (res.count, n, res.error)
+    if args.full:
+        check_rows(torch, rows, res, files, vsz, rl, first_seq)
     counters = ctx.last_counters()
 
     run, timings = ctx.prepare_scan(views, rows)
@@ -476,14 +539,18 @@ def main():
 
     # the timed loop issues the same C call a compiled caller would (arguments built once); each
     # step's phase times (HIP events inside the library) are copied out of the context after it
-    elapsed, tt = time_loop(torch, dev, run, timings, args.steps, barrier, dist, args.dist_backend)
+    elapsed, tt, last_count = time_loop(torch, dev, run, timings, args.steps, barrier, dist, args.dist_backend)
     ms_per_step = elapsed * 1e3 / args.steps
+    dumped = None
+    if args.dump_outputs:  # the row arrays as the last timed step left them (nothing has run since)
+        dumped = dump_outputs(torch, args.dump_outputs, rows, last_count, prefix=f"rank{rank}_" if world > 1 else "",
+                              sample_rows=DUMP_SAMPLE_ROWS // world)
     # The first call over a file set (a real Cask::open scans each set once, cask.rs:346-382): the
     # timed steps reuse the context's per-set state — the region probe (k_probe_regions) and the file
     # table already on the device — so a call over another set in between makes the next full call
     # pay both again. Reported beside `value`, never in it.
     cold = []
-    for _ in range(0 if args.no_cold else 3):
+    for _ in range(3 if args.full and not args.no_cold else 0):
         ctx.scan_device(views[:1], rows)
         torch.cuda.synchronize(dev)
         t_c = time.perf_counter()
@@ -504,7 +571,7 @@ def main():
     achieved = bytes_per_step / (k_avg * 1e-3) / 1e9  # algorithmic GB/s of the dominant kernel
     traffic, traffic_src = load_traffic(kname)
     # the read-only stream ceiling over the same bytes, beside the roofline (not in `value`)
-    ceiling = stream_ceiling(torch, dev, views) if rank == 0 else None
+    ceiling = stream_ceiling(torch, dev, views) if rank == 0 and args.full else None
     names = ["pipeline_ms", "hash_or_chunk_scan_ms", "long_ms", "validate_ms", "repair_ms", "compact_ms",
              "search_ms", "chase_ms"]
     breakdown = {nm: sum(t[i] for t in tt) / len(tt) for i, nm in enumerate(names)}
@@ -540,6 +607,9 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": ms_per_step,
+            "full": args.full,
+            "dumped_outputs": ({"dir": args.dump_outputs, "bytes": dumped, "rows": int(last_count)}
+                               if args.dump_outputs else None),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -592,7 +662,7 @@ def main():
             print(json.dumps(out), flush=True)
 
     watchdog = None
-    if rank == 0 and dist is not None:
+    if rank == 0 and dist is not None and args.full:
         def fire():
             emit(dict(extra), f"the multi-rank secondary measurements did not finish within {args.secondary_timeout:.0f} s; "
                               f"the line was printed without the ones still running")
@@ -605,7 +675,7 @@ def main():
 
     # N>1: this rank's keydir block and the blocks' gather + rank-0 fold over RCCL through the C ABI
     # (cask_keydir_gather_rccl), reported apart from the metric; a failure is reported, not fatal
-    if dist is not None and not args.no_gather:
+    if dist is not None and args.full and not args.no_gather:
         try:
             from cask_amd.keydir import shard_keydir
             # every rank's record count (ranks' Zipf draws differ): all of them are live keys
@@ -657,7 +727,7 @@ def main():
             extra["keydir_gather_error"] = f"{type(e).__name__}: {e}"[:300]
 
     # N>1: SURVEY's cfg5 shard per rank and the key-hash partitioned keydir (reported beside the metric)
-    if dist is not None and not args.no_cfg5:
+    if dist is not None and args.full and not args.no_cfg5:
         # (the workload is kept by `zf` whatever happens inside; only the generator's views are dropped
         # for the shard's memory, and the rows are rebuilt after it, failed or not)
         zf = (files, vsz, rl)
@@ -675,7 +745,7 @@ def main():
             extra["rescan_error"] = f"{type(e).__name__}: {e}"[:300]
 
     # end-to-end: host-resident files -> H2D -> scan -> rows D2H (cask_scan_host), first 2 files
-    if rank == 0 and not args.no_e2e and res is not None:
+    if rank == 0 and args.full and not args.no_e2e and res is not None:
         host = [(f.file_id, f.data.cpu().numpy()) for f, _ in files[:2]]
         ctx.scan_host(host[:1])
         te = time.perf_counter()
@@ -688,19 +758,19 @@ def main():
         del host, hr
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline([f for f, _ in files], max(1, min(args.cpu_sample_files, len(files))), cfg)
         line["cpu_baseline"] = cpu
 
-    if rank == 0 and world == 1 and not (args.no_cfg1 and args.no_shard_n1):
+    if rank == 0 and world == 1 and args.full and not (args.no_cfg1 and args.no_shard_n1):
         res = None
         rows = views = None
         files = vsz = rl = None
         run = timings = None
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_shard_n1:
+    if rank == 0 and world == 1 and args.full and not args.no_shard_n1:
         secondary(extra, "configs4_shard_n1", lambda: cfg4_shard_n1_secondary(ctx, torch, dev, args.steps))
-    if rank == 0 and world == 1 and not args.no_cfg1:
+    if rank == 0 and world == 1 and args.full and not args.no_cfg1:
         extra["configs1_secondary"] = cfg1_secondary(ctx, torch, dev, max(10, args.steps))
 
     if watchdog is not None:

@@ -1,7 +1,8 @@
 """Multi-rank path on CPU (gloo, world_size 2): file sharding, the max-sequence all-reduce, the
 gather of the ranks' keydir blocks and rank 0's native fold of them. Blocks come from
 the oracle's restatement here (no GPU in this container; tests/test_scan_gpu.py checks that the
-device builds the same bytes); on the GPU box the same functions run over RCCL (bench.py --gpus N).
+device builds the same bytes); on a node with GPUs the same functions run over RCCL
+(bench.py --gpus N --full).
 
 Rank 0 folds only what it received — no data file is read there — and the result must equal a
 single-process replay of the same directory (cask.rs:346-382), including stale tombstones whose

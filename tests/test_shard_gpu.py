@@ -231,7 +231,7 @@ def test_rccl_c_abi_gather_single_rank(gpu_ctx, tmp_path):
     """cask_keydir_gather_rccl on a one-rank communicator made through the C ABI (unique id, comm
     init): the rank's block goes to itself and is folded there; keydir, stats and sequence equal the
     replay, and the gathered byte count and max sequence are reported. (Two or more ranks need as
-    many GPUs: bench.py --gpus N runs it on the driver's node.)"""
+    many GPUs: bench.py --gpus N --full runs it on the driver's node.)"""
     import torch
     from cask_amd.distributed import RcclComm, gather_fold_rccl, rccl_unique_id
     path = str(tmp_path / "db")
@@ -292,7 +292,7 @@ def test_device_partition_equals_host(gpu_ctx, tmp_path, seed):
 def test_rccl_c_abi_exchange_single_rank(gpu_ctx, tmp_path):
     """cask_keydir_exchange_rccl on a one-rank communicator: the block is partitioned on the device
     (one part), sent to itself, folded and finished from its own terms — the replay's keydir, stats
-    and sequence. (More ranks need as many GPUs: bench.py --gpus N runs it on the driver's node.)"""
+    and sequence. (More ranks need as many GPUs: bench.py --gpus N --full runs it on the driver's node.)"""
     import torch
     from cask_amd.distributed import RcclComm, exchange_fold_rccl, rccl_unique_id
     path = str(tmp_path / "db")

@@ -14,7 +14,7 @@ step() {
   if [ $rc -ne 0 ]; then echo "STOP after $name (rc=$rc)"; exit $rc; fi
 }
 if [ -z "$SKIP_BENCH" ]; then
-  TAILN=1 step bench_full 600 python bench.py
+  TAILN=1 step bench_full 600 python bench.py --full
 fi
 export TMPDIR=/tmp
 B="$R/bench.py --steps ${PSTEPS:-20} --warmup ${PWARM:-3} --no-cpu-baseline --no-e2e --no-cfg1 --no-shard-n1 --no-cold"
