@@ -123,7 +123,7 @@ class ScanContext:
             assert t.is_cuda and t.dtype.itemsize == 1 and t.is_contiguous()
             views[i].file_id = int(fid)
             views[i].flags = L.VIEW_DEVICE
-            views[i].data = t.data_ptr() if t.numel() else None
+            views[i].data = t.data_ptr() or None  # (an empty torch tensor has no address)
             views[i].len = t.numel()
         r = L.Rows()
         r.capacity = rows["pos"].numel()
@@ -160,7 +160,7 @@ class ScanContext:
             assert t.is_cuda and t.dtype.itemsize == 1 and t.is_contiguous()
             views[i].file_id = int(fid)
             views[i].flags = L.VIEW_DEVICE
-            views[i].data = t.data_ptr() if t.numel() else None
+            views[i].data = t.data_ptr() or None  # (an empty torch tensor has no address)
             views[i].len = t.numel()
         if rows is None:
             rows = self.alloc_rows(self.rows_bound([t.numel() for _, t in files]))

@@ -75,7 +75,9 @@ const char* cask_ctx_last_error(const cask_ctx* ctx);
 /* Chunk size in bytes used by the scan kernels (the unit of speculation and staging). */
 uint32_t cask_scan_chunk_bytes(void);
 
-/* A data file to scan: `{:010}.cask.data` contents (log.rs:473-476), no header/footer. */
+/* A data file to scan: `{:010}.cask.data` contents (log.rs:473-476), no header/footer.
+ * `data` may have any alignment, and the files of a call may be slices of one allocation with
+ * other bytes (other files' included) right before and behind them; only [data, data + len) counts. */
 #define CASK_VIEW_DEVICE 1u /* data points to device memory (else host memory) */
 typedef struct cask_file_view {
   uint32_t file_id;
@@ -87,7 +89,9 @@ typedef struct cask_file_view {
 /* Rows in (file, pos) order, struct-of-arrays. One row per record the reference iterator
  * yields: Ok records, InvalidChecksum records (iteration continues past them, log.rs:467-471)
  * and at most one trailing UnexpectedEof record per file (iteration ends there).
- * The key of row i lives at data[pos[i] + 18 .. + ksz[i]] of its file (not copied). */
+ * The key of row i lives at data[pos[i] + 18 .. + ksz[i]] of its file (not copied).
+ * The five arrays need only their element types' natural alignment and may be slices of larger
+ * allocations: nothing outside [0, capacity) of any of them is written. */
 typedef struct cask_rows {
   uint64_t capacity; /* in: slots in every array */
   uint64_t count;    /* out: rows produced (also set on CASK_E_CAPACITY = rows needed) */

@@ -14,10 +14,13 @@ import cask_ref as R
 pytestmark = pytest.mark.gpu
 
 
-def _check(ctx, bodies):
+def _check(ctx, bodies, files=None):
+    """files: the bodies already placed on the device, [(i + 1, uint8 view)] in the bodies' order."""
     import torch
-    files = [(i + 1, torch.from_numpy(np.frombuffer(b, np.uint8).copy()).cuda() if b else
-              torch.empty(0, dtype=torch.uint8, device="cuda")) for i, b in enumerate(bodies)]
+    if files is None:
+        files = [(i + 1, torch.from_numpy(np.frombuffer(b, np.uint8).copy()).cuda() if b else
+                  torch.empty(0, dtype=torch.uint8, device="cuda")) for i, b in enumerate(bodies)]
+    assert [(fid, t.numel()) for fid, t in files] == [(i + 1, len(b)) for i, b in enumerate(bodies)]
     res = ctx.parse_hints_device(files)
     got_all = [t[:res.count].cpu().numpy() for t in (res.pos, res.seq, res.ksz, res.vsz, res.status)]
     first = None
@@ -101,3 +104,38 @@ def test_many_small_bodies(gpu_ctx, tmp_path):
     bodies = _bodies_of(path)
     assert len(bodies) > 100
     _check(gpu_ctx, bodies)
+
+
+def _hint_filler(rng, n):
+    """Exactly n bytes of a valid hint body: whole hints, or, for n < 22, the leading bytes of one."""
+    out, seq = [], 9_000_000
+    while n >= 22:
+        ksz = n - 22 if n < 100 else rng.randrange(0, 40)  # (what is left after it holds a hint)
+        out.append(R.hint_bytes(seq, rng.randbytes(ksz), rng.randrange(0, 400), rng.random() < 0.1, 18 * seq))
+        seq += 1
+        n -= 22 + ksz
+    if n:
+        out.append(R.hint_bytes(seq, rng.randbytes(7), 5, False, 18 * seq)[:n])
+    return b"".join(out)
+
+
+def test_arena_hint_bodies(gpu_ctx, tmp_path):
+    """The hint bodies of a written log (keys of 0-40 B and a few of 60,000 B) as slices of one
+    arena (test_scan_gpu.arena), one at each of its 16 offsets past a 256-B boundary, inside one
+    continuous valid hint body: whole hints, or the leading bytes of one, right before and behind
+    every body. One more body cut inside a record, the rest of that record right behind it."""
+    from test_scan_gpu import ARENA_OFFSETS, arena
+    rng = random.Random(9)
+    path = str(tmp_path / "db")
+    R.write_log(path, _entries(rng, 12000, big_key_p=0.002), max_file_size=192 << 10)
+    bodies = _bodies_of(path)
+    assert len(bodies) >= len(ARENA_OFFSETS)
+    bodies = bodies[:len(ARENA_OFFSETS)]
+    assert sum(len(b) > 60000 for b in bodies) >= 3  # bodies with a 60,000-B key
+    recs = R.hint_offsets(bodies[3])
+    cut = recs[len(recs) // 2][0] + 10
+    bodies.append(bodies[3][:cut])
+    after = [b""] * len(ARENA_OFFSETS) + [bodies[3][cut:]]
+    files, _back = arena(bodies, list(ARENA_OFFSETS) + [13], "live", after, filler=_hint_filler)
+    res = _check(gpu_ctx, bodies, files)
+    assert res.error is not None and res.error.file_id == len(bodies)

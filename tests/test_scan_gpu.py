@@ -57,13 +57,20 @@ def oracle_rows(buf):
     return [[int(r["pos"]), int(r["seq"]), int(r["ksz"]), int(r["vsz_raw"]), int(r["status"])] for r in rows], rows
 
 
-def check_against_oracle(ctx, bufs, device=False):
-    """Scan `bufs` (list of bytes) in one call; compare every row and the first error."""
+def check_against_oracle(ctx, bufs, device=False, tens=None, rows=None):
+    """Scan `bufs` (list of bytes) in one call; compare every row and the first error. `tens`: the
+    same bytes already placed on the device, [(file_id, uint8 view)] (then a device scan); `rows`:
+    the caller's row arrays (device scans)."""
     files = list(enumerate(bufs, start=1))
+    if tens is not None:
+        assert [t.numel() for _, t in tens] == [len(b) for b in bufs]
+        files = [(fid, b) for (fid, _), b in zip(tens, bufs)]
+        device = True
     if device:
         import torch
-        tens = [(fid, torch.from_numpy(np.frombuffer(b, np.uint8).copy()).cuda()) for fid, b in files]
-        res = ctx.scan_device(tens)
+        if tens is None:
+            tens = [(fid, torch.from_numpy(np.frombuffer(b, np.uint8).copy()).cuda()) for fid, b in files]
+        res = ctx.scan_device(tens, rows)
         res.pos, res.seq, res.vsz, res.ksz, res.status = [t[:res.count].cpu().numpy() for t in
                                                           (res.pos, res.seq, res.vsz, res.ksz, res.status)]
     else:
@@ -355,7 +362,7 @@ def test_zipf_sizes_long_records(gpu_ctx, seed):
     assert cnt["walked"] == 0, cnt
 
 
-@pytest.mark.parametrize("seqs", ["rising", "shuffled", "jumps", "corrupt"])
+@pytest.mark.parametrize("seqs", ["rising", "shuffled", "jumps", "corrupt", "high"])
 def test_walk_search_long_stretches(gpu_ctx, seqs):
     """k_walk_search where a run's first short record lies behind stretches of 4-8 records of ~64 KiB
     (>= 30 windows of 8 KiB): the probe follows the long candidates' chains header to header to the
@@ -364,9 +371,11 @@ def test_walk_search_long_stretches(gpu_ctx, seqs):
     jumping by 2^33 at every stretch, it must fall back to the windows; with a byte flipped in some
     of the short records behind the stretches (their checksums fail) it must move on to a later
     candidate. Rows and the first error equal the oracle's row for row (24 MiB: many 1-MiB runs
-    start inside a stretch)."""
+    start inside a stretch). "high": rising sequences at the top of the range the reference accepts
+    (from 2^64 - 2 - 4,000; 2^64 - 1 overflows its sequence + 1), where the rule's difference must
+    still come out right."""
     rng = random.Random(0x5EA)
-    recs, seq, bad = [], 1, []
+    recs, seq, bad = [], (1 << 64) - 2 - 4000 if seqs == "high" else 1, []
     seqlist = list(range(1, 4000))
     if seqs == "shuffled":
         rng.shuffle(seqlist)
@@ -389,6 +398,7 @@ def test_walk_search_long_stretches(gpu_ctx, seqs):
             seq += 1
             total += len(recs[-1])
     assert seqs != "corrupt" or bad
+    assert seq - 1 <= (1 << 64) - 2  # the last sequence used stays inside the reference's domain
     buf = b"".join(recs)
     check_against_oracle(gpu_ctx, [buf, buf[: len(buf) // 2 + 12345]], device=True)
     cnt = gpu_ctx.last_counters()
@@ -641,6 +651,371 @@ def test_engine_scan_path_large(native, tmp_path):
     for fid in R.find_data_files(path):
         with open(R.hint_file_path(path, fid), "rb") as a, open(R.hint_file_path(ref_dir, fid), "rb") as b:
             assert a.read() == b.read()
+
+
+# ------------------------------------------------- caller buffers at every alignment (the C ABI
+# promises none): files as slices of one arena with other bytes right before and behind them
+ARENA_OFFSETS = (0, 1, 2, 3, 4, 7, 8, 9, 15, 16, 17, 31, 33, 63, 65, 127)
+ARENA_PAD = 128 << 10  # (a header of 0xFF bytes read as a record spans 18 + 65,535 bytes)
+ARENA_FILLS = ("zero", "ones", "live")
+
+
+def record_filler(rng, n):
+    """Exactly n bytes of a valid log: whole records that verify, or, for n < 18, the leading bytes
+    of a valid record's header."""
+    out, seq = [], 7_000_000
+    while n >= 18:
+        size = n if n < 736 else rng.randrange(18, 700)  # (what is left after it holds a record)
+        ksz = min(rng.randrange(0, 24), size - 18)
+        out.append(R.entry_new(seq, rng.randbytes(ksz), rng.randbytes(size - 18 - ksz)).write_bytes())
+        assert len(out[-1]) == size
+        seq += 1
+        n -= size
+    if n:
+        out.append(R.entry_new(seq, rng.randbytes(5), rng.randbytes(40)).write_bytes()[:n])
+    return b"".join(out)
+
+
+class EmptyAt:
+    """A file of length 0 at a real device address (torch gives an empty view no address)."""
+    is_cuda = True
+    dtype = np.dtype(np.uint8)
+
+    def __init__(self, ptr):
+        self._ptr = ptr
+
+    def numel(self):
+        return 0
+
+    def is_contiguous(self):
+        return True
+
+    def data_ptr(self):
+        return self._ptr
+
+
+def arena(bufs, offsets, fill, after=None, filler=record_filler):
+    """One uint8 device tensor holding every file of `bufs`: file i is the contiguous view that
+    starts offsets[i] bytes past a 256-B boundary, with at least 64 KiB before the first file and
+    behind the last, so that a read of a whole granule, line or window past a file's ends stays
+    inside the allocation: a wrong read gives a wrong answer, never a fault. `fill` is what
+    surrounds the files: "zero", "ones" (0xFF), or "live": the arena is one valid log (`filler`
+    makes its records) around the files, the gap before a file (whatever brings it to its offset,
+    0-255 B) one verifying record or, under 18 B, the leading bytes of a valid header; after[i]
+    (the bytes a cut file lost) then follows file i directly, so a reader that runs past `len`
+    finds the record complete. Returns ([(file_id, view)], the tensor that owns the memory)."""
+    import torch
+    assert len(bufs) == len(offsets) and fill in ARENA_FILLS
+    rng = random.Random(0xA7E4A)
+    parts, starts, cur = [], [], 0
+
+    def gap(n):
+        nonlocal cur
+        if n:
+            parts.append(filler(rng, n) if fill == "live" else bytes([0xFF if fill == "ones" else 0]) * n)
+            assert len(parts[-1]) == n
+        cur += n
+
+    gap(ARENA_PAD)
+    for i, (b, off) in enumerate(zip(bufs, offsets)):
+        assert 0 <= off < 256
+        gap((off - cur) % 256)
+        starts.append(cur)
+        parts.append(bytes(b))
+        cur += len(b)
+        if fill == "live" and after is not None and after[i]:
+            parts.append(after[i])
+            cur += len(after[i])
+    gap(ARENA_PAD + (-cur) % 256)
+    host = b"".join(parts)
+    assert len(host) == cur
+    back = torch.empty(cur + 256, dtype=torch.uint8, device="cuda")
+    whole = back[-back.data_ptr() % 256:][:cur]
+    assert whole.data_ptr() % 256 == 0
+    whole.copy_(torch.from_numpy(np.frombuffer(host, np.uint8).copy()))
+    views = []
+    for i, (b, s, off) in enumerate(zip(bufs, starts, offsets)):
+        assert host[s:s + len(b)] == bytes(b)
+        assert s >= ARENA_PAD and s + len(b) + ARENA_PAD <= cur
+        t = whole[s:s + len(b)] if len(b) else EmptyAt(whole.data_ptr() + s)
+        assert t.data_ptr() % 128 == off % 128 and t.data_ptr() % 256 == off and t.is_contiguous()
+        assert back.data_ptr() <= t.data_ptr() - ARENA_PAD
+        assert t.data_ptr() + len(b) + ARENA_PAD <= back.data_ptr() + back.numel()
+        views.append((i + 1, t))
+    return views, back
+
+
+_arena_inputs = {}
+
+
+def _cached(name, make):
+    """The inputs of an arena test, built once for its nine runs (three modes x three fills)."""
+    if name not in _arena_inputs:
+        _arena_inputs[name] = make()
+    return _arena_inputs[name]
+
+
+def _cut_ends(rng, files, seq):
+    """File ends, cycled: on a record boundary; 7 bytes short (inside the last record's tail); inside
+    the last record's 18-B header; a last record (a tombstone) whose key ends on the file's last
+    byte. Returns the files and the bytes each one lost."""
+    bufs, after = [], []
+    for i, b in enumerate(files):
+        kind, lost = i % 4, b""
+        if kind == 1:
+            b += R.entry_new(seq + i, rng.randbytes(9), rng.randbytes(40)).write_bytes()
+            b, lost = b[:-7], b[-7:]
+        elif kind == 2:
+            last = R.entry_new(seq + i, rng.randbytes(9), rng.randbytes(40)).write_bytes()
+            keep = rng.randrange(1, 18)
+            b, lost = b + last[:keep], last[keep:]
+        elif kind == 3:
+            b += R.entry_deleted(seq + i, rng.randbytes(rng.randrange(1, 20))).write_bytes()
+        bufs.append(b)
+        after.append(lost)
+    return bufs, after
+
+
+def _arena_short():
+    rng = random.Random(0xA1)
+    files = []
+    for i in range(len(ARENA_OFFSETS)):
+        b = bytearray(make_records(rng, 620, lambda r: r.randrange(0, 31), lambda r: r.randrange(0, 601),
+                                   seq0=1 + 1000 * i, tomb_p=0.05))
+        assert len(b) >= 6 * 32768 - 20000
+        if i in (2, 7, 12):
+            b[rng.randrange(len(b))] ^= 1 << rng.randrange(8)
+        files.append(bytes(b))
+    return _cut_ends(rng, files, 500_000)
+
+
+@pytest.mark.parametrize("fill", ARENA_FILLS)
+def test_arena_short_records(gpu_ctx, fill):
+    """16 files of short records (~200 KiB: interior 32-KiB chunk boundaries) as slices of one
+    arena, one at each offset of ARENA_OFFSETS past a 256-B boundary (every residue mod 4, the 16-B
+    granule edges, the 128-B line edges): the chunk scan's shifted windows (chunk_at: shift != 0,
+    the extra granule, the whole-window branch) with zero, 0xFF or verifying records of another file
+    right before and behind every file; three files with a flipped byte, every kind of file end.
+    Rows and the first error as the oracle's scan of each slice's own bytes."""
+    bufs, after = _cached("short", _arena_short)
+    tens, _back = arena(bufs, ARENA_OFFSETS, fill, after)
+    res = check_against_oracle(gpu_ctx, bufs, tens=tens)
+    assert res.error is not None
+    cnt = gpu_ctx.last_counters()
+    print(f"arena_short[{fill}]: geometry {cnt['geometry']} walk_mode {cnt['walk_mode']} "
+          f"repaired_chunks {cnt['repaired_chunks']} dense_path {cnt['dense_path']}")
+    if os.environ.get("CASK_SCAN_MODE") is None:
+        assert cnt["walk_mode"] == 0, cnt
+
+
+def _arena_long():
+    rng = random.Random(0xA2)
+    vsz = _zipf_vsz(rng)
+    files, seq = [], 1
+    for i, off in enumerate(ARENA_OFFSETS):
+        want = (2560 << 10) if i % 4 == 1 else (300 << 10)  # four files of >= 2 walk runs of 1 MiB
+        recs, n = [], 0
+        while n < want:
+            k = rng.randbytes(16)
+            e = R.entry_deleted(seq, k) if rng.random() < 0.02 else R.entry_new(seq, k, rng.randbytes(vsz(rng)))
+            recs.append(bytearray(e.write_bytes()))
+            n += len(recs[-1])
+            seq += 1
+        for r in rng.sample(recs, 3):
+            if i % 4 != 3 and len(r) > 40:
+                r[34 + rng.randrange(len(r) - 34)] ^= 1 << rng.randrange(8)  # in the record's value
+        if i == 5:  # a record over 2 KiB as the last one of a file whose end is not 16-B aligned
+            last = 3000 + (1 if (off + n + 34 + 3000) % 16 == 0 else 0)
+            recs.append(bytearray(R.entry_new(seq, rng.randbytes(16), rng.randbytes(last)).write_bytes()))
+            n += len(recs[-1])
+            seq += 1
+            assert (off + n) % 16 != 0 and len(recs[-1]) > 2048
+        files.append(b"".join(bytes(r) for r in recs))
+    after = [b""] * len(files)
+    files[10], after[10] = files[10][:-7], files[10][-7:]  # cut 7 bytes short
+    assert sum(len(f) >= 2 << 20 for f in files) == 4
+    return files, after
+
+
+@pytest.mark.parametrize("fill", ARENA_FILLS)
+def test_arena_long_records(gpu_ctx, fill):
+    """The same with configs[2]'s Zipf value sizes (four files of 2.5 MiB: two walk runs and more;
+    the rest 300 KiB): the walk's staging (walk_stage, k_walk_hash's sl), k_run_hash's rounds of
+    whole 128-B lines and the chase's last-granule rule at file bases and ends of every alignment,
+    with another file's bytes right behind each end; flipped bytes in record values, a file cut 7
+    bytes short, a record over 2 KiB ending a file off the 16-B grid."""
+    bufs, after = _cached("long", _arena_long)
+    tens, _back = arena(bufs, ARENA_OFFSETS, fill, after)
+    res = check_against_oracle(gpu_ctx, bufs, tens=tens)
+    assert res.error is not None
+    cnt = gpu_ctx.last_counters()
+    print(f"arena_long[{fill}]: geometry {cnt['geometry']} walk_mode {cnt['walk_mode']} "
+          f"repaired_chunks {cnt['repaired_chunks']} dense_path {cnt['dense_path']} walked {cnt['walked']}")
+    if os.environ.get("CASK_SCAN_MODE") in (None, "walk"):
+        assert cnt["walk_mode"] >= 1, cnt
+
+
+def _arena_tiny():
+    rng = random.Random(0xA3)
+    whole = R.entry_new(77, rng.randbytes(5), rng.randbytes(40)).write_bytes()
+    tiny = [(whole[:n], whole[n:]) for n in (0, 1, 3, 15, 17, 18, 19)]
+    tiny.append((R.entry_deleted(78, b"").write_bytes(), b""))  # a whole record of 18 bytes
+    tiny.append((R.entry_new(79, b"", b"").write_bytes(), b""))  # and one with an empty value
+    assert [len(t) for t, _ in tiny] == [0, 1, 3, 15, 17, 18, 19, 18, 18]
+    normal = [make_records(rng, 130, lambda r: r.randrange(0, 31), lambda r: r.randrange(0, 601), seq0=1000 * (i + 1),
+                           tomb_p=0.05) for i in range(2)]
+    bufs, after, offs = [normal[0]], [b""], [3]
+    for j, (t, rest) in enumerate(tiny):
+        # inside one 16-B granule where it fits (else from a granule's start); across a granule
+        # edge; across a 128-B line edge
+        for off in (1 if len(t) <= 15 else 0, 15, 127):
+            bufs.append(t)
+            after.append(rest)
+            offs.append(off)
+        if j == 4:
+            bufs.append(normal[1])
+            after.append(b"")
+            offs.append(9)
+    for t, off in zip(bufs, offs):
+        if 2 <= len(t) < 32768:
+            assert (off % 16 + len(t) > 16) == (off != 1), (off, len(t))
+    return bufs, after, offs
+
+
+@pytest.mark.parametrize("fill", ARENA_FILLS)
+def test_arena_tiny_files(gpu_ctx, fill):
+    """Files of 0 (at a real address), 1, 3, 15, 17, 18 and 19 bytes (the leading bytes of a valid
+    record, the rest of it right behind them in the live arena), a whole 18-B tombstone with an
+    empty key and a whole 18-B record with an empty value, each inside one granule, across a granule
+    edge and across a line edge, among two normal files: the staging of a file inside one granule
+    (k_walk_hash's sl < 0) and of windows shorter than a granule's shift. Mostly UnexpectedEof
+    rows; the first error as the oracle's."""
+    bufs, after, offs = _cached("tiny", _arena_tiny)
+    tens, _back = arena(bufs, offs, fill, after)
+    assert tens[1][1].numel() == 0 and tens[1][1].data_ptr() != 0
+    res = check_against_oracle(gpu_ctx, bufs, tens=tens)
+    assert res.error is not None and res.error.kind == 2
+
+
+def _guarded_rows(cap, shift):
+    """Row arrays of `cap` elements that start shift[name] elements into backing tensors of cap + 2
+    elements filled with a sentinel. Returns (rows, check): check() asserts that every backing
+    element outside the views still holds the sentinel."""
+    import torch
+    spec = {"pos": (torch.int64, 0x5A5A5A5A5A5A5A5A), "seq": (torch.int64, 0x5A5A5A5A5A5A5A5A),
+            "vsz": (torch.int32, 0x5A5A5A5A), "ksz": (torch.int16, 0x5A5A), "status": (torch.uint8, 0x5A)}
+    back = {k: torch.full((cap + 2,), v, dtype=dt, device="cuda") for k, (dt, v) in spec.items()}
+    rows = {k: back[k][shift[k]:shift[k] + cap] for k in spec}
+
+    def check():
+        for k, (_dt, v) in spec.items():
+            b = back[k].cpu().numpy()
+            outside = np.concatenate([b[:shift[k]], b[shift[k] + cap:]])
+            assert len(outside) == 2 and (outside == v).all(), (k, outside)
+
+    return rows, check
+
+
+def _rows_inputs():
+    rng = random.Random(0xA4)
+    short = bytearray(make_records(rng, 2500, lambda r: r.randrange(0, 31), lambda r: r.randrange(0, 601), tomb_p=0.05))
+    short[len(short) // 3] ^= 0x04
+    zipf = bytearray(make_records(rng, 700, lambda r: 16, _zipf_vsz(rng), seq0=10_000, tomb_p=0.02))
+    zipf[len(zipf) // 2] ^= 0x20
+    return bytes(short), bytes(zipf)[:-7]
+
+
+@pytest.mark.parametrize("which", ["all", "status"])
+def test_rows_arrays_unaligned(gpu_ctx, which):
+    """Row arrays that are slices of larger allocations, one element in: pos/seq 8 mod 16, vsz 4 mod
+    16, ksz 2 mod 8, status 1 mod 4 ("all"), or only status off its alignment ("status": any one
+    array must switch the dense rows to the element-wise stores, ScanArgs::vec_ok). A short-record
+    file and a Zipf file: the rows as the oracle's, and the elements right before and behind every
+    array untouched."""
+    for buf in _cached("rows", _rows_inputs):
+        cap = gpu_ctx.rows_bound([len(buf)])
+        shift = {k: 1 if which == "all" or k == "status" else 0 for k in ("pos", "seq", "vsz", "ksz", "status")}
+        rows, check = _guarded_rows(cap, shift)
+        mod = {k: (rows[k].data_ptr() % m) for k, m in (("pos", 16), ("seq", 16), ("vsz", 16), ("ksz", 8), ("status", 4))}
+        assert mod == ({"pos": 8, "seq": 8, "vsz": 4, "ksz": 2, "status": 1} if which == "all" else
+                       {"pos": 0, "seq": 0, "vsz": 0, "ksz": 0, "status": 1}), mod
+        res = check_against_oracle(gpu_ctx, [buf], device=True, rows=rows)
+        assert res.error is not None
+        check()
+
+
+# ------------------------------------------------------------- walk-mode repair (k_restride)
+_MIB = 1 << 20
+
+
+def _embedded_log(variant):
+    """Outer records (16-B keys, at most 40 KiB) whose values are 12-59 serialized valid records of
+    300-933 B with rising sequences, 6 MiB in all. Returns the bytes and, checked here on the host:
+    every interior 1-MiB boundary strictly inside an outer value; fewer than kWalkSlotCap (128)
+    record starts, outer and embedded together, in every 32-KiB chunk."""
+    rng = random.Random(0xAD5)
+    outer, inner_at, pos, seq = [], [], 0, 1
+    while pos < 6 * _MIB:
+        inner, at, size = [], [], 34
+        for _ in range(rng.randrange(12, 60)):
+            e = R.entry_new(1_000_000 + seq, rng.randbytes(16), rng.randbytes(rng.randrange(266, 900))).write_bytes()
+            seq += 1
+            assert 300 <= len(e) <= 933
+            if size + len(e) > 40 << 10:
+                break
+            at.append(pos + size)
+            inner.append(e)
+            size += len(e)
+        rec = R.entry_new(len(outer) + 1, rng.randbytes(16), b"".join(inner)).write_bytes()
+        assert len(rec) == size and len(inner) >= 12
+        outer.append((pos, size, rec))
+        inner_at.append(at)
+        pos += size
+    buf = bytearray(b"".join(r for _, _, r in outer))
+    bounds = list(range(_MIB, len(buf), _MIB))
+    assert len(bounds) >= 5
+    holder = []  # the outer record each run boundary lies in
+    for b in bounds:
+        j = next(j for j, (p, n, _) in enumerate(outer) if p <= b < p + n)
+        assert outer[j][0] + 34 < b < outer[j][0] + outer[j][1], b  # (a) strictly inside its value
+        holder.append(j)
+    per_chunk = np.bincount(np.array([p for p, _, _ in outer] + [p for at in inner_at for p in at]) // 32768)
+    assert per_chunk.max() < 128, per_chunk.max()  # (b) no slot-row overflow: the redo cannot be what ran
+    if variant == "corrupt":
+        j = next(j for j in range(5, len(outer)) if j not in holder)
+        buf[outer[j][0] + 18 + 3] ^= 0x10  # an outer key: that row's checksum status must survive
+        first = next(p for p in inner_at[holder[0]] if p >= bounds[0])  # first embedded record of run 1
+        buf[first + 18 + 16 + 5] ^= 0x02  # (in its value): the search must move on
+    if variant == "cut":
+        del buf[-7:]
+    return bytes(buf), len(outer), len(bounds), int(per_chunk.max())
+
+
+@pytest.mark.parametrize("variant", ["clean", "corrupt", "cut"])
+def test_walk_repair_keeps_small_slot_rows(gpu_ctx, variant):
+    """A walk-mode call that needs the repair path while its slot rows are the small ones
+    (kWalkSlotCap per chunk): every 1-MiB run but the first starts inside a value made of valid
+    records short enough for k_walk_search to verify and accept as the run's start, so validation
+    fails, k_restride moves the rows found so far to the full stride and the exact re-scans repair
+    the flagged chunks. No chunk holds 128 record starts, so it is not the slot-overflow redo. Rows
+    and the first error as the oracle's (which sees the outer records only); then an ordinary Zipf
+    file on the same context, which now holds the swapped slot buffers."""
+    buf, nouter, nbounds, most = _cached("embedded_" + variant, lambda: _embedded_log(variant))
+    want = O.scan(buf)
+    assert len(want) == nouter  # (c) the oracle finds only the outer records
+    assert int((want["status"] != 0).sum()) == {"clean": 0, "corrupt": 2, "cut": 1}[variant]
+    check_against_oracle(gpu_ctx, [buf], device=True)
+    cnt = gpu_ctx.last_counters()
+    print(f"walk_repair[{variant}]: outer {nouter} boundaries {nbounds} max starts/chunk {most} walk_mode "
+          f"{cnt['walk_mode']} repaired_chunks {cnt['repaired_chunks']} dense_path {cnt['dense_path']} "
+          f"walked {cnt['walked']} geometry {cnt['geometry']}")
+    if cnt["walk_mode"] == 1:
+        assert cnt["repaired_chunks"] > 0 and cnt["dense_path"] == 0 and cnt["walked"] == 0, cnt
+    if os.environ.get("CASK_SCAN_MODE") == "walk":
+        assert cnt["walk_mode"] == 1, cnt
+    zipf = _cached("after_repair", lambda: make_records(random.Random(0xAD6), 600, lambda r: 16,
+                                                         _zipf_vsz(random.Random(0)), tomb_p=0.02))
+    check_against_oracle(gpu_ctx, [zipf], device=True)
 
 
 # ------------------------------------------------------------------------------------ encoder

@@ -15,10 +15,14 @@ import cask_shard as S
 pytestmark = pytest.mark.gpu
 
 
-def _make_db(path, seed, nfiles=6, nrec=3000, nkeys=400, tomb_p=0.12, back_p=0.1, max_vsz=300):
-    """Data files of overwrites, deletes and out-of-order sequences (stale records)."""
+def _make_db(path, seed, nfiles=6, nrec=3000, nkeys=400, tomb_p=0.12, back_p=0.1, max_vsz=300, seq0=0, keys=None,
+             last_tomb=False):
+    """Data files of overwrites, deletes and out-of-order sequences (stale records). seq0 is added
+    to every sequence; keys replaces the generated key set; last_tomb ends every file with a
+    tombstone of a non-empty key (the key's last byte is the file's last)."""
     rng = random.Random(seed)
-    keys = [rng.randbytes(rng.randrange(0, 24)) for _ in range(nkeys)]
+    if keys is None:
+        keys = [rng.randbytes(rng.randrange(0, 24)) for _ in range(nkeys)]
     seq = 1
     os.makedirs(path, exist_ok=True)
     for fid in range(1, nfiles + 1):
@@ -28,11 +32,15 @@ def _make_db(path, seed, nfiles=6, nrec=3000, nkeys=400, tomb_p=0.12, back_p=0.1
             s = seq if rng.random() > back_p else max(0, seq - rng.randrange(1, 5000))
             seq += 1
             if rng.random() < tomb_p:
-                recs.append(R.entry_deleted(s, k).write_bytes())
+                recs.append(R.entry_deleted(seq0 + s, k).write_bytes())
             else:
-                recs.append(R.entry_new(s, k, rng.randbytes(rng.randrange(0, max_vsz))).write_bytes())
+                recs.append(R.entry_new(seq0 + s, k, rng.randbytes(rng.randrange(0, max_vsz))).write_bytes())
+        if last_tomb:
+            recs.append(R.entry_deleted(seq0 + seq, rng.choice([k for k in keys if k])).write_bytes())
+            seq += 1
         with open(R.data_file_path(path, fid), "wb") as f:
             f.write(b"".join(recs))
+    return seq0 + seq - 1  # the highest sequence a record can carry
 
 
 def _files(path):
@@ -43,10 +51,13 @@ def _files(path):
     return out
 
 
-def _device_block(ctx, part):
+def _device_block(ctx, part, tens=None):
+    """tens: the files of `part` already placed on the device, [(file_id, uint8 view)]."""
     import torch
     from cask_amd.keydir import shard_keydir
-    tens = [(fid, torch.from_numpy(np.frombuffer(b, np.uint8).copy()).cuda()) for fid, b in part]
+    if tens is None:
+        tens = [(fid, torch.from_numpy(np.frombuffer(b, np.uint8).copy()).cuda()) for fid, b in part]
+    assert [(fid, t.numel()) for fid, t in tens] == [(fid, len(b)) for fid, b in part]
     res = ctx.scan_device(tens)
     assert res.error is None
     return shard_keydir(ctx, tens, {"pos": res.pos, "seq": res.seq, "vsz": res.vsz, "ksz": res.ksz,
@@ -308,3 +319,83 @@ def test_rccl_c_abi_exchange_single_rank(gpu_ctx, tmp_path):
         assert sent == 0 and got == blk.numel()
     finally:
         comm.close()
+
+
+# ------------------------------------------------- files as slices of one arena (any alignment)
+@pytest.fixture(scope="module")
+def edge_db(tmp_path_factory):
+    """4 files x 2,500 records (and a last tombstone whose key ends on the file's last byte) over
+    keys of 0-18, 31-33 and 255 bytes and all-zero keys of 0-17 bytes (they differ only in ksz and
+    share one gathered prefix); its oracle block and replay, computed once for the three fills."""
+    rng = random.Random(0xED6E)
+    keys = [rng.randbytes(n) for n in list(range(0, 19)) + [31, 32, 33, 255] for _ in range(12)]
+    keys += [bytes(n) for n in range(0, 18)]
+    path = str(tmp_path_factory.mktemp("edge") / "db")
+    top = _make_db(path, 21, nfiles=4, nrec=2500, keys=keys, last_tomb=True)
+    assert top <= (1 << 64) - 2
+    files = _files(path)
+    for _, b in files:
+        rows = R.scan_entries(b)
+        assert rows[-1].deleted and rows[-1].ksz > 0 and rows[-1].pos + 18 + rows[-1].ksz == len(b)
+        # a key's first 16 bytes are read as the aligned dwords around them: keys of every length
+        # 1-16 at all four residues of (pos + 18) % 4, in every file (whatever base it is placed at)
+        seen = {(r.ksz, (r.pos + 18) % 4) for r in rows}
+        assert all((n, a) in seen for n in range(1, 17) for a in range(4))
+    return path, files, _oracle_block(files), _want(path)
+
+
+@pytest.mark.parametrize("fill", ["zero", "ones", "live"])
+def test_arena_keydir_block(gpu_ctx, edge_db, fill, monkeypatch):
+    """The keydir block of files that are slices of one arena, at offsets 1, 2, 3 and 127 past a
+    256-B boundary and with zero, 0xFF or another file's verifying records around them: k_kd_hash
+    reads a key's first 16 bytes from the aligned dwords that hold them and masks them, so what
+    lies in those dwords outside the key (the next file's first bytes behind a key that ends its
+    file) must not reach the hash, the gathered prefix or the block. Byte for byte the
+    restatement's block; and, with every key in one hash segment (CASK_KD_HASH_BITS=0: keys told
+    apart by their gathered bytes and lengths alone), two shards' fold equal to the replay."""
+    from test_scan_gpu import arena
+    from cask_amd.keydir import KeydirFold
+    path, files, want_block, want = edge_db
+    views, _back = arena([b for _, b in files], [1, 2, 3, 127], fill)
+    tens = [(fid, t) for (fid, _), (_, t) in zip(files, views)]
+    assert _device_block(gpu_ctx, files, tens) == want_block
+    monkeypatch.setenv("CASK_KD_HASH_BITS", "0")
+    fold = KeydirFold()
+    for lo, hi in ((0, 1), (1, 4)):
+        fold.merge(_device_block(gpu_ctx, files[lo:hi], tens[lo:hi]))
+    with fold.finish() as db:
+        assert _got(db) == want
+
+
+# ------------------------------------------------------- sequences over the whole u64 range
+_HIGH_ROWS = 3 * 1500
+
+
+@pytest.mark.parametrize("seq0", [0, (1 << 32) - 30, (1 << 63) - 100, (1 << 64) - 2 - _HIGH_ROWS],
+                         ids=["0", "2^32", "2^63", "top"])
+def test_device_block_high_sequences(gpu_ctx, tmp_path, monkeypatch, seq0):
+    """Sequences up to 2^64 - 2 (the reference's sequence + 1, cask.rs:379, overflows past it), a
+    key's history straddling 2^32 and 2^63: the device keeps seq + 1 (k_kd_hash, k_kd_segs), splits
+    sequences into two dwords and the Python side carries them as int64. The block byte for byte the
+    restatement's, the two-shard fold and open() with the device and the host fold equal to the
+    replay, current_sequence included."""
+    from cask_amd import CaskOptions
+    from cask_amd.keydir import KeydirFold
+    path = str(tmp_path / "db")
+    top = _make_db(path, 23, nfiles=3, nrec=1500, nkeys=200, seq0=seq0)
+    assert top == seq0 + _HIGH_ROWS <= (1 << 64) - 2  # inside the reference's domain
+    files = _files(path)
+    want = _want(path)
+    assert want[2] - 1 > seq0 and want[2] <= (1 << 64) - 1
+    assert _device_block(gpu_ctx, files) == _oracle_block(files)
+    fold = KeydirFold()
+    for part in (files[:1], files[1:]):
+        fold.merge(_device_block(gpu_ctx, part))
+    with fold.finish() as db:
+        assert _got(db) == want
+    for devfold in ("1", "0"):
+        for h in (tmp_path / "db").glob("*.cask.hint"):
+            h.unlink()  # both opens take the scan path
+        monkeypatch.setenv("CASK_OPEN_DEVFOLD", devfold)
+        with CaskOptions().open(path) as db:
+            assert _got(db) == want, devfold

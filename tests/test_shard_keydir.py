@@ -4,6 +4,7 @@ native fold (cask_keydir_merge / cask_keydir_finish through the C ABI) must give
 Cask::open keydir, stats and sequence (cask.rs:346-382, 60-90; stats.rs:23-48) for any split of the
 files into contiguous shards — stale tombstones and resurrections included."""
 import random
+from dataclasses import replace
 
 import pytest
 from hypothesis import given, settings, strategies as st
@@ -98,17 +99,25 @@ def _native_fold(native, blocks, many=False):
 @pytest.mark.parametrize("threads", [1, 5])
 @pytest.mark.parametrize("seed", range(12))
 def test_native_fold_matches(native, seed, threads, monkeypatch):
-    """threads=5: the merge on threads by keydir table (CASK_PAR_FOLD_MIN=0 forces it)."""
+    """threads=5: the merge on threads by keydir table (CASK_PAR_FOLD_MIN=0 forces it). Each input
+    with a base added to every sequence: 0, and bases that bring the sequences across 2^32, across
+    2^63 and up to 2^64 - 2, the highest the reference accepts (its sequence + 1, cask.rs:379,
+    overflows past it); current_sequence - 1 against the in-order fold's highest sequence too."""
     monkeypatch.setenv("CASK_PAR_FOLD_MIN", "0" if threads > 1 else str(1 << 62))
     monkeypatch.setenv("CASK_HOST_THREADS", str(threads))
     rng = random.Random(100 + seed)
-    files = _random_files(rng, 7, 60, rng.choice([2, 10, 50]), 0.25, 0.25)
-    want = _full_fold(files)
-    for cuts in ([0, 7], [0, 3, 7], [0, 1, 2, 4, 7]):
-        for many in (False, True):
-            got = _native_fold(native, _blocks(files, cuts), many)
-            assert got[0] == want[0] and got[1] == want[1]
-            assert got[2] == max(want[2], 0)
+    base_files = _random_files(rng, 7, 60, rng.choice([2, 10, 50]), 0.25, 0.25)
+    nrows = sum(len(rows) for _, rows in base_files)
+    for base in (0, (1 << 32) - 30, (1 << 63) - 100, (1 << 64) - 2 - nrows):
+        files = [(f, [replace(r, seq=r.seq + base) for r in rows]) for f, rows in base_files]
+        assert all(0 <= r.seq <= (1 << 64) - 2 for _, rows in files for r in rows)
+        want = _full_fold(files)
+        for cuts in ([0, 7], [0, 3, 7], [0, 1, 2, 4, 7]):
+            for many in (False, True):
+                got = _native_fold(native, _blocks(files, cuts), many)
+                assert got[0] == want[0] and got[1] == want[1], base
+                assert got[2] == max(want[2], 0), base
+                assert S.fold_blocks(_blocks(files, cuts)) == want, base
 
 
 def test_native_fold_rejects_bad_blocks(native):
