@@ -1,4 +1,4 @@
-// Host-side helpers shared by the engine (engine.cpp) and the runtime (scan_runtime.cpp): the host
+// Host-side helpers shared by the engine (engine_*.cpp) and the runtime (scan_runtime.cpp): the host
 // thread count, a fork/join over threads, and a ring of pinned staging buffers that moves pageable
 // host memory to and from the device on several threads at once (a copy between pageable memory
 // and the device goes through the driver's own staging at ~10-25 GB/s).
@@ -38,7 +38,7 @@ inline unsigned host_threads() {
 // be created (std::system_error) has its share run on the calling thread, so the result does not
 // depend on how many threads actually ran. An exception thrown by any share (std::bad_alloc under
 // memory pressure) is caught on its thread and the first one is rethrown here once every thread
-// has been joined: it reaches the entry point's own handler (engine.cpp: abi_status / abi_db) instead of
+// has been joined: it reaches the entry point's own handler (engine_db.h: abi_status / abi_db) instead of
 // std::terminate, and no thread is left running over the caller's state.
 template <class F>
 void parallel_for(unsigned nt, F fn) {

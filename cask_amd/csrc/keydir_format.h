@@ -1,6 +1,6 @@
 // The keydir block of one shard: what a rank of the multi-GPU replay sends to rank 0 (SURVEY.md
 // §8e). Built on the device by cask_shard_keydir (k_keydir.hip), folded on the host by
-// cask_keydir_merge (engine.cpp). Little-endian, 8-byte aligned:
+// cask_keydir_merge (engine_keydir.cpp). Little-endian, 8-byte aligned:
 //   ShardHeader | ShardRec[nrec] | ShardFileStat[nfiles] | key bytes of the records, in record order
 // Records of one key appear in the shard's replay order (file id, pos).
 //

@@ -1,5 +1,5 @@
 """cask_shard.py — restatement of the shard keydir block (cask_amd/csrc/k_keydir.hip,
-keydir_format.h) and of rank 0's fold (engine.cpp cask_keydir_merge / cask_keydir_finish).
+keydir_format.h) and of rank 0's fold (engine_keydir.cpp cask_keydir_merge / cask_keydir_finish).
 TEST INFRASTRUCTURE ONLY: the gloo tests build blocks with it on the CPU, the GPU tests compare the
 device's blocks with it byte for byte, and the property tests check the whole scheme against the
 reference's in-order fold (Index::update, cask.rs:60-90; Stats, stats.rs:23-48) restated in
@@ -184,8 +184,8 @@ def key_owner(k: bytes, nparts: int) -> int:
 
 
 def partition_block(b: bytes, nparts: int) -> list[bytes]:
-    """Restatement of the key-hash partition (keydir_format.h; k_keydir.hip kd_partition, engine.cpp
-    cask_keydir_partition_host): part o = the records whose key's owner is o, in block order, their
+    """Restatement of the key-hash partition (keydir_format.h; k_keydir.hip kd_partition,
+    engine_keydir.cpp cask_keydir_partition_host): part o = the records whose key's owner is o, in block order, their
     keys, and the stats table (counts in part 0 only)."""
     (magic, ver, nrec, kb, nfiles, _, maxp1, rows_in, total, _) = HDR.unpack_from(b, 0)
     assert magic == MAGIC and ver == VERSION

@@ -2,7 +2,7 @@
 // page cache (/dev/shm) to the device? Compares, over NF files of 1 GiB:
 //   dma   H2D from pinned buffers only (no file reads): the copy engines' ceiling
 //   pread T threads pread into pinned 32-MiB buffers, no copy to the device
-//   ring  pread + H2D, two pinned buffers per thread (engine.cpp's read_to_device)
+//   ring  pread + H2D, two pinned buffers per thread (engine_dev.cpp's read_to_device)
 //   reg   mmap each file, hipHostRegister it in pieces, H2D straight from the page cache (no CPU copy)
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/read_bench.cpp -o tools/read_bench
 //   tools/read_bench [dir] [nfiles] [threads]
